@@ -12,7 +12,13 @@ barrier around the timed region and the MAX-reduction of the elapsed time.
 `python -m torch.distributed.run` (a child process started before anything touches the GPU);
 under torchrun (WORLD_SIZE set) every rank checks WORLD_SIZE == N and that RCCL sees N ranks.
 
-Prints ONE JSON line (rank 0).  The engine runs the encoder as two half-batch streams (its
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it builds the
+engine and the batch, warms up, times `--steps` steps, writes the last step's outputs if
+`--dump-outputs DIR` is given (DIR/probs.npy: the float32 [B, 1] probabilities Engine.score
+returned; same arguments = same inputs, so two builds compare output for output) and prints the
+line.  Everything below is measured only with `--full`, after the headline and in the same line.
+
+The engine runs the encoder as two half-batch streams (its
 default); `roofline` is the dominant kernel (the FFN1 GEMM, [T,768]x[768,3072] + bias + GELU)
 timed with HIP events on its launch stream (events created before the timed steps) in a
 single-stream pass over the same batch right after the timed region, so that no other kernel
@@ -57,6 +63,14 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--precision", default="f32x3", choices=["fp32", "f32x3", "bf16"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as "
+                         "DIR/probs.npy (float32 [batch, 1]; rank r of N > 1: probs_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other measurement: roofline / "
+                         "attention kernel timing, fp32 and bf16 modes, CPU baselines, "
+                         "microbenchmarks and the attack legs (the options below shape them; "
+                         "without --full none of them runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="CPU scoring microbenchmark budget (cpu_baseline)")
     ap.add_argument("--cpu-e2e-seconds", type=float, default=60.0,
@@ -832,6 +846,52 @@ def microbench_leg(dev, precision, steps, warmup, world):
     return out
 
 
+def dump_outputs(dirname, probs, rank, world):
+    """--dump-outputs: what Engine.score returned in the last timed step (float32 [B, C]) as
+    DIR/probs.npy; with N > 1 ranks every rank scores its own batch and writes
+    DIR/probs_rank<r>.npy."""
+    import numpy as np
+
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "probs.npy" if world == 1 else f"probs_rank{rank}.npy"
+    np.save(d / name, np.ascontiguousarray(probs, dtype=np.float32))
+
+
+def headline(args, world, elapsed, probs, peak):
+    """The result line of the timed steps alone (a plain run prints exactly this; --full adds the
+    other measurements to it)."""
+    import numpy as np
+
+    B, L = args.batch, args.seq
+    total_q = world * args.steps * B
+    executed = executed_flops_per_query(L) * total_q / elapsed / 1e12
+    return {
+        "metric": METRIC,
+        "value": round(total_q / elapsed, 3),
+        "unit": "victim queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"fp32": "fp32", "f32x3": "f32x3 (fp32 operands as bf16 hi+lo, 3 bf16 MFMAs "
+                                           "per product, f32 accumulate; |dp| vs fp32 <= 1e-4)",
+                  "bf16": "bf16 (f32 accumulate / residual)"}[args.precision],
+        "precision_mode": args.precision,
+        "data": "synthetic (seeded RoBERTa-base weights; uniform token ids; no checkpoint offline)",
+        "config": {"workload": "CodeBERT Devign victim scoring of one GA mutant population per "
+                               "step (config 2 shape: eval_batch_size 64 x block 512)",
+                   "global_batch": B * world, "seq_len": L,
+                   "parallelism": f"dp{world} (example shards)"},
+        "whole_step_executed_tflops": round(executed, 3),
+        "whole_step_frac_of_peak": round(executed / world / peak, 4),
+        "probs_checksum": float(np.round(probs.astype(np.float64).sum(), 6)),
+    }
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     args = parse_args()
@@ -889,6 +949,24 @@ def main():
     # the headline: the production engine with no instrumentation in the timed steps
     elapsed, _ = time_steps(eng, ids_dev, lens, out, args.steps, args.warmup, dev, dist,
                             profile=False)
+    out_host = out.cpu().numpy()  # what the last timed step returned to its caller
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_host, rank, world)
+    # roofline peak of the arithmetic the GEMMs run: f32 MFMA; bf16 MFMA; split-bf16 issues
+    # 3 bf16 MFMAs per product, so its ceiling in algorithmic FLOP/s is the bf16 peak / 3
+    peak = {"fp32": FP32_MFMA_PEAK_TFLOPS, "bf16": BF16_MFMA_PEAK_TFLOPS,
+            "f32x3": BF16_MFMA_PEAK_TFLOPS / 3}[args.precision]
+    if not args.full:  # the plain run ends here: the headline alone
+        if dist is not None:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=COLL_DEV)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        eng.close()
+        if rank == 0:
+            print(json.dumps(headline(args, world, elapsed, out_host[:, 0], peak)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # FFN1 launch times inside the two-stream engine (context only), on separate steps
     _, (s_ms, s_n, s_flop) = time_steps(eng, ids_dev, lens, out, max(5, args.steps // 2), 1,
                                         dev, dist, profile=True)
@@ -919,15 +997,10 @@ def main():
         dist.all_reduce(kt, op=dist.ReduceOp.SUM)
         k_ms, k_n, k_flop, s_ms, s_n = float(kt[0]), int(kt[1]), float(kt[2]), float(kt[3]), int(kt[4])
 
-    probs = out.cpu().numpy()[:, 0]
-    total_q = world * args.steps * B
-    value = total_q / elapsed
+    probs = out_host[:, 0]
+    value = world * args.steps * B / elapsed
     per_launch_s = (k_ms / 1e3) / max(k_n, 1)
     achieved = (k_flop / max(k_n, 1)) / per_launch_s / 1e12 if k_n else None
-    # roofline peak of the arithmetic the GEMMs run: f32 MFMA; bf16 MFMA; split-bf16 issues
-    # 3 bf16 MFMAs per product, so its ceiling in algorithmic FLOP/s is the bf16 peak / 3
-    peak = {"fp32": FP32_MFMA_PEAK_TFLOPS, "bf16": BF16_MFMA_PEAK_TFLOPS,
-            "f32x3": BF16_MFMA_PEAK_TFLOPS / 3}[args.precision]
     attention = attention_summary(at_ms, at_n, n1, B, L, peak,
                                   f"single-stream engine, the same batch, {n1} steps")
     fp32_mode = bf16_mode = None
@@ -965,28 +1038,9 @@ def main():
                                                            - b_out.cpu().numpy()[:, 0]).max()),
                 "note": "diagnostic only: 1 bf16 MFMA per product instead of 3"}
             b_eng.close()
-    executed = executed_flops_per_query(L) * total_q / elapsed / 1e12
-    res = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "victim queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": {"fp32": "fp32", "f32x3": "f32x3 (fp32 operands as bf16 hi+lo, 3 bf16 MFMAs "
-                                           "per product, f32 accumulate; |dp| vs fp32 <= 1e-4)",
-                  "bf16": "bf16 (f32 accumulate / residual)"}[args.precision],
-        "precision_mode": args.precision,
+    res = headline(args, world, elapsed, probs, peak)
+    res.update({
         "max_abs_dprob_vs_fp32_mode": fp32_mode["max_abs_dprob_vs_this_mode"] if fp32_mode else None,
-        "data": "synthetic (seeded RoBERTa-base weights; uniform token ids; no checkpoint offline)",
-        "config": {"workload": "CodeBERT Devign victim scoring of one GA mutant population per "
-                               "step (config 2 shape: eval_batch_size 64 x block 512)",
-                   "global_batch": B * world, "seq_len": L,
-                   "parallelism": f"dp{world} (example shards)"},
         "roofline": {
             "bound": "mfma",
             "kernel": {"fp32": "gemm_f32_nt_kernel<EPI_BIAS_GELU>",
@@ -1008,10 +1062,7 @@ def main():
             "two_stream_avg_launch_us": round(1e3 * s_ms / max(s_n, 1), 2) if s_n else None,
         },
         "attention": attention,
-        "whole_step_executed_tflops": round(executed, 3),
-        "whole_step_frac_of_peak": round(executed / world / peak, 4),
-        "probs_checksum": float(np.round(probs.astype(np.float64).sum(), 6)),
-    }
+    })
     if fp32_mode:
         res["fp32_mode"] = fp32_mode
     if bf16_mode:

@@ -6,8 +6,9 @@
 #   tests     pytest -m gpu            (K=<-k filter>, MAXFAIL=<n>, default -x; KEEPGOING=1: go on
 #             to the next step after test failures, never after a crash / abort / time limit)
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py $BENCH_FULL_ARGS        (the default run: every leg)
-#   short     scoring-only bench, 20 steps             ($BENCH_ARGS appended)
+#   bench     python bench.py --full $BENCH_FULL_ARGS (every leg)
+#   short     scoring-only bench (--full without the CPU and attack legs), 20 steps
+#             ($BENCH_ARGS appended)
 #   trace     rocprofv3 --kernel-trace --stats over the scoring-only bench
 #   pmc       one rocprofv3 --pmc pass per ';'-separated group in $PASSES over the scoring-only bench
 #   gemm      tools/gemm_bench.py   (S=shapes, V=variants, ROUNDS)
@@ -18,7 +19,7 @@ cd "$GRAFT_REPO_ROOT"
 TAG=${1:?tag}; shift
 OUT="$GRAFT_REPO_ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-SHORT="$GRAFT_REPO_ROOT/bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-fp32-mode --attack-examples 0 --subs-seconds 0 --mhm-examples 0 --aa-examples 0 --clone-examples 0 --no-config1 ${BENCH_ARGS:-}"
+SHORT="bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-fp32-mode --attack-examples 0 --subs-seconds 0 --mhm-examples 0 --aa-examples 0 --clone-examples 0 --no-config1 ${BENCH_ARGS:-}"
 run() {  # name limit cmd...
   local name=$1 lim=$2; shift 2
   echo "== $name ($(date +%T))"
@@ -43,8 +44,8 @@ for S in "$@"; do
            fi
            if [ $rc -ne 0 ] && ! { [ "${KEEPGOING:-0}" = 1 ] && [ $rc -eq 1 ]; }; then exit $rc; fi ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 1000 python -u bench.py ${BENCH_FULL_ARGS:-} || exit $? ;;
-    short) run short 400 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline --attack-examples 0 --subs-seconds 0 --mhm-examples 0 --aa-examples 0 --clone-examples 0 --no-config1 ${BENCH_ARGS:-} || exit $? ;;
+    bench) run bench 1000 python -u bench.py --full ${BENCH_FULL_ARGS:-} || exit $? ;;
+    short) run short 400 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --attack-examples 0 --subs-seconds 0 --mhm-examples 0 --aa-examples 0 --clone-examples 0 --no-config1 ${BENCH_ARGS:-} || exit $? ;;
     trace) run trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $SHORT || exit $? ;;
     pmc)
       IFS=';' read -ra PS <<< "${PASSES:-FETCH_SIZE;WRITE_SIZE}"

@@ -48,6 +48,39 @@ def test_single_stream_engine_is_a_config_not_the_environment(monkeypatch):
     assert dict(os.environ) == before
 
 
+def test_headline_is_the_timed_steps_alone(monkeypatch):
+    """The plain run's line: value and ms_per_step come from --steps timed steps of B queries
+    (value · ms_per_step = 1000 · B · ranks), and no other measurement's key is in it."""
+    import numpy as np
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert not args.full and args.dump_outputs is None
+    probs = np.linspace(0.1, 0.9, args.batch, dtype=np.float32)
+    h = bench.headline(args, 1, 0.105, probs, 838.9)
+    assert h["metric"] == bench.METRIC and h["unit"] == "victim queries/s"
+    assert h["higher_is_better"] is True and h["dtype"].startswith("f32x3")
+    assert h["steps"] == 7 and h["ms_per_step"] == 15.0
+    assert h["value"] == round(7 * 64 / 0.105, 3)
+    assert h["probs_checksum"] == float(np.round(probs.astype(np.float64).sum(), 6))
+    assert not {"roofline", "attention", "fp32_mode", "cpu_baseline", "microbench",
+                "attack"} & set(h)
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: the step's [B, C] probabilities as DIR/probs.npy (one file per rank when
+    there are several), float32, DIR created on demand."""
+    import numpy as np
+
+    p = np.random.default_rng(0).random((64, 1)).astype(np.float32)
+    bench.dump_outputs(tmp_path / "a" / "b", p, 0, 1)
+    got = np.load(tmp_path / "a" / "b" / "probs.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, p)
+    bench.dump_outputs(tmp_path / "a" / "b", p.astype(np.float64), 1, 2)
+    got = np.load(tmp_path / "a" / "b" / "probs_rank1.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, p)
+
+
 def test_pmc_traffic_comes_from_the_newest_round():
     """roofline.traffic: the committed FETCH / WRITE summary of the newest round for the
     precision (r<round><letters>_ ordering: r4z after r4k after r3ap after r3z)."""
